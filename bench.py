@@ -19,7 +19,14 @@ database, exchanges transposed edges (all-to-all-v) and all-gathers the updated 
 rank holds ITS ROW SHARD of X when the timed region starts (``sharded_input=True``; ``--replicated-input`` hands every
 rank the full block instead) and the line carries ``phases_ms`` (shard gather, kNN pieces, exchanges, symmetrisation,
 init, loop -- HIP events, max over ranks), ``allgather_us`` (one per-iteration row exchange, timed on its own after the
-run), ``rccl_context`` and ``hbm_peak_gb`` per rank.
+run; ``--full``), ``rccl_context`` and ``hbm_peak_gb`` per rank.
+
+A plain run sets up, warms up, times ``--steps`` steps, writes the last step's embedding with ``--dump-outputs DIR`` and
+prints its line.  ``--full`` then also runs the legs the headline figure does not need: the kNN context searches
+(``knn_context``, ``knn_uniform``), the BASELINE configs C3 / C5 (``configs``), ``cpu_baseline`` and, at N > 1, the
+``allgather_us`` timing; it writes the line's long objects to ``--detail-file`` as well.
+
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
   roofline     -- the dominant kernel group of the step, measured with HIP events inside the timed region: the UMAP
@@ -27,8 +34,8 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with two extra o
                   evaluation vs 8 TB/s) when the loop outweighs the kNN build, else the kNN scan (algorithmic flops
                   2*n_q*N*D per launch vs the matrix peak of the pipe it runs on); the other one is reported as
                   roofline_secondary;
-  cpu_baseline -- the CPU oracle (row-chunked torch/MKL restatement of the reference's backend=None
-                  path, oracle/ref_torch.py) timed on this box's host cores on a bounded sample.
+  cpu_baseline -- (--full) the CPU oracle (row-chunked torch/MKL restatement of the reference's backend=None
+                  path, oracle/ref_torch.py) timed on the host's cores on a bounded sample.
 """
 
 import argparse
@@ -279,6 +286,23 @@ def config_c3(dev, width=15, steps=1, iters=500):
     }
 
 
+def dump_outputs(out_dir, Z, limit=60_000_000, seed=0):
+    """--dump-outputs: the embedding the last timed fit_transform returned, as DIR/embedding.npy (float32).  Above `limit`
+    bytes, a fixed seeded sample of its rows instead: DIR/embedding_sample.npy (float32) and DIR/embedding_rows.npy (the
+    sampled row indices, ascending, float64)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    Z = Z.detach().float().cpu()
+    if Z.numel() * 4 <= limit:
+        np.save(os.path.join(out_dir, "embedding.npy"), Z.numpy())
+        return
+    n_rows = limit // (8 + 4 * Z.shape[1])
+    rows = torch.randperm(Z.shape[0], generator=torch.Generator().manual_seed(seed))[:n_rows].sort().values
+    np.save(os.path.join(out_dir, "embedding_sample.npy"), Z[rows].numpy())
+    np.save(os.path.join(out_dir, "embedding_rows.npy"), rows.double().numpy())
+
+
 def _committed_traffic(fname, *path):
     """HBM-side bytes per launch from a PMC summary committed under profiles/ (separate rocprofv3 --pmc passes over the same
     kernel at the same shape in an earlier round; the kernels have not changed since), or None."""
@@ -360,10 +384,18 @@ def main():
     ap.add_argument("--neighbors", dest="k", type=int, default=30)
     ap.add_argument("--max-iter", type=int, default=1000)
     ap.add_argument("--scale", type=float, default=2.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need, after the timed steps: the kNN context searches, the "
+                         "BASELINE configs C3 / C5, the CPU baseline, the row-exchange timing (N > 1) and the detail file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the embedding the last timed fit_transform returned to DIR/embedding.npy "
+                         "(float32; above 60 MB a fixed seeded row sample, DIR/embedding_sample.npy + DIR/embedding_rows.npy)")
+    ap.add_argument("--detail-file", default=os.path.join("bench_out", "bench_detail.json"),
+                    help="--full: where the full line is also written (relative paths are taken from the repository root)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-knn-variants", action="store_true",
-                    help="skip the untimed kNN context figures (unpruned two-stage, one-stage fp32, structureless data)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the untimed BASELINE configs C3 (LargeVis 1M) and C5 (SEA 200k)")
+                    help="--full: skip the untimed kNN context figures (unpruned two-stage, one-stage fp32, structureless data)")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the untimed BASELINE configs C3 (LargeVis 1M) and C5 (SEA 200k)")
     ap.add_argument("--loop", choices=["auto", "graph", "c", "python"], default="auto",
                     help="UMAP loop driver: replayed HIP graphs (default), plain launches from the C loop object, or one Python iteration per step")
     ap.add_argument("--replicated-input", action="store_true",
@@ -379,6 +411,8 @@ def main():
                          "exchange served from the other ranks' graphs, the row exchange as a loopback copy) and print its phase split")
     ap.add_argument("--world", type=int, default=8)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.emulate_rank is not None:
         from tools.rank_share import measure
@@ -488,14 +522,19 @@ def main():
     torch.cuda.reset_peak_memory_stats(dev)
     phases.start()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        one_step(True)
+    for i in range(args.steps):
+        Z = one_step(True)
+        if i + 1 < args.steps or not args.dump_outputs:
+            Z = None    # only the last step's embedding is kept, and only for --dump-outputs
         knn_events.extend(dbase.PROFILE)
         grad_events.extend(umod.PROFILE)
         loop_events.extend(umod.LOOP_PROFILE)
     barrier()
     elapsed = time.perf_counter() - t0
     phase_ms = {k_: v / args.steps for k_, v in phases.stop().items()}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, Z)
+    Z = None
     dbase.PROFILE = None
     umod.PROFILE = None
     umod.LOOP_PROFILE = None
@@ -514,6 +553,7 @@ def main():
     if distributed:
         allreduce_max_(hbm_peak)
         allreduce_max_(ph)      # every rank records the same phase names (same code path)
+    if distributed and args.full:
         # one per-iteration row exchange of the (N, 2) embedding, on its own: the transport the loop used
         from torchdr_amd.parallel import RcclContext, allgather_rows_
 
@@ -686,26 +726,28 @@ def main():
             detail["loop_in_cluster_order"] = bool(keep.get("loop_order"))
             detail["allgather_us"] = allgather_us
             detail["allgather_ms_per_fit"] = None if allgather_us is None else allgather_us * args.max_iter * 1e-3
-        if not args.no_knn_variants and world == 1:
+        if args.full and not args.no_knn_variants and world == 1:
             detail["knn_context"] = knn_variants(X, args, dbase)
             detail["knn_uniform"] = knn_uniform(args, dev, dbase)
-        if not args.no_configs and world == 1:
+        if args.full and not args.no_configs and world == 1:
             del X
             torch.cuda.empty_cache()
             detail["configs"] = {"c3": config_c3(dev), "c5": config_c5(dev),
                                  "note": "BASELINE.json configs[2] and configs[4], run once each after the timed region; per-kernel roofline "
                                          "by HIP events around the C-ABI entry point on the launch stream"}
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(X_cpu, args.k, args.max_iter, keep, budget_s=args.cpu_budget)
             detail["cpu_baseline_detail"] = dict(cpu)
         detail_file = None
-        try:
-            os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-            detail_file = os.path.join("gpurun_out", "bench_detail.json")
-            json.dump(detail, open(os.path.join(ROOT, detail_file), "w"), indent=1)
-        except OSError:
-            detail_file = None
+        if args.full:
+            try:
+                path = os.path.join(ROOT, args.detail_file)
+                os.makedirs(os.path.dirname(path), exist_ok=True)
+                json.dump(detail, open(path, "w"), indent=1)
+                detail_file = args.detail_file
+            except OSError:
+                detail_file = None
         out = dict(detail)
         out["detail_file"] = detail_file
         out.update({

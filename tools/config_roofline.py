@@ -1,5 +1,5 @@
 """BASELINE configs C3 and C5 as JSON objects with a `roofline` each (the code lives in bench.py: `config_c3`, `config_c5`; the
-default `python bench.py` run emits both under `configs`):
+`python bench.py --full` run emits both under `configs`):
 
     python tools/config_roofline.py c3     # LargeVis N = 1M, D = 128, kNN width 15 (perplexity 5), 500 iterations
     python tools/config_roofline.py c3b    # the same with kNN width 45

@@ -31,7 +31,7 @@ for sz in $SIZES; do
     for X in rccl peer; do
       [ "$W" = 1 ] && [ "$X" = peer ] && continue
       FLAG=""; [ "$X" = peer ] && FLAG="--peer-exchange"
-      timeout 1200 python bench.py --gpus $W --npoints $N --dim $D --max-iter $ITERS --steps 2 --warmup 1 --no-cpu-baseline --no-knn-variants --no-configs $FLAG \
+      timeout 1200 python bench.py --gpus $W --npoints $N --dim $D --max-iter $ITERS --steps 2 --warmup 1 --full --no-cpu-baseline --no-knn-variants --no-configs $FLAG \
           > "$OUT/bench_n${N}_w${W}_${X}.json" 2> "$OUT/bench_n${N}_w${W}_${X}.err"
       echo "{\"step\": \"bench n=$N d=$D gpus=$W exchange=$X\", \"rc\": $?}" >> "$OUT/steps.jsonl"
     done

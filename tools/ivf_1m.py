@@ -1,5 +1,5 @@
-import sys, torch, json, time
-sys.path.insert(0, "/root/repo")
+import os, sys, torch, json, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tests.conftest import gmm
 from torchdr_amd.distance import FaissConfig, pairwise_distances
 def recall(I, Ie):

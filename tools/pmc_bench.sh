@@ -3,7 +3,7 @@
 # separate rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) with --kernel-trace only, as MI355X_MICROARCH.md prescribes.
 #   gpurun --timeout 900 -- 'bash tools/pmc_bench.sh r06'      -> gpurun_out/r06_umap_pool_pmc.json (copy to profiles/)
 export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
 TAG=${1:-r06}
 mkdir -p $R/gpurun_out
 cd /tmp

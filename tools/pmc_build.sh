@@ -2,7 +2,7 @@
 # PMC passes over umap_sched_build_kernel (one window of 32 iterations at N = 1M, production numbering):
 #   gpurun --timeout 600 -- 'bash tools/pmc_build.sh'
 export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p $R/gpurun_out
 cd /tmp
 i=0

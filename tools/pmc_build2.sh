@@ -2,7 +2,7 @@
 # PMC passes over umap_sched_build2_kernel (windows of 32 iterations at N = 1M, production numbering):
 #   gpurun --timeout 900 -- 'bash tools/pmc_build2.sh [stage]'
 export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
 STAGE=${1:-0}
 mkdir -p $R/gpurun_out
 cd /tmp

@@ -3,7 +3,7 @@
 #   gpurun --timeout 900 -- 'bash tools/pmc_configs.sh'
 # (separate --pmc runs with --kernel-trace only, as the guide prescribes; summaries in gpurun_out/pmc_configs.txt)
 export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p $R/gpurun_out
 cd /tmp
 for c in c3 c5; do

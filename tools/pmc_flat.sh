@@ -1,7 +1,7 @@
 #!/bin/bash
 # PMC passes over the threshold-scan kernel (N = 1M, one term): gpurun -- 'bash tools/pmc_flat.sh [terms]'
 export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
 T=${1:-1}
 O=$R/gpurun_out/pmc_flat_${T}; mkdir -p $O
 cd /tmp

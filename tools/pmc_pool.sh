@@ -2,7 +2,7 @@
 # Counters of the pool-sampled gradient launch (csrc/tdr_umap_pool.hip) on the N = 1M graph: separate rocprofv3 --pmc passes with
 # --kernel-trace only.   gpurun --timeout 900 -- 'bash tools/pmc_pool.sh [geom]'
 export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
 G=${1:-0}
 mkdir -p $R/gpurun_out
 cd /tmp

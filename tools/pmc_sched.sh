@@ -2,7 +2,7 @@
 # PMC passes over the scheduled UMAP kernels: gpurun -- 'bash tools/pmc_sched.sh "1 2 3 4 5 6 7 8"'
 # (separate --pmc runs, --kernel-trace only, as the guide prescribes; summaries go to gpurun_out/pmc_sched.txt)
 export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp
 i=0
 SEL=${1:-"1 2 3 4 5"}

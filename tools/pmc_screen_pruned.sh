@@ -1,7 +1,7 @@
 #!/bin/bash
 # PMC passes over the cluster-pruned two-stage kNN (N=1M, headline data): gpurun -- 'bash tools/pmc_screen_pruned.sh'
 export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp
 i=0
 for grp in "GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVES" \

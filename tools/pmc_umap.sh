@@ -1,7 +1,7 @@
 #!/bin/bash
 # PMC passes over the UMAP gradient kernels: gpurun -- 'bash tools/pmc_umap.sh'
 export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp
 i=0
 SEL=${1:-"1 2 3"}

@@ -2,7 +2,7 @@
 # Kernel trace of ONE emulated rank's fit (rank r of W alone on this GPU): which kernels its share consists of.
 #   gpurun --timeout 900 -- 'bash tools/rank_share_trace.sh 4000000 256 4 8 c4'
 export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
 N=${1:-1000000}; D=${2:-128}; RANK=${3:-4}; W=${4:-8}; TAG=${5:-1m}
 mkdir -p $R/gpurun_out
 cd /tmp
