@@ -661,6 +661,38 @@ int tdr_add_scaled_f64(double* grad, const double* F, const double* S, double co
 int tdr_sgd_step_f64(double* Z, const double* grad, double* buf, int64_t n, double lr, double momentum, int first, int* nan_flag,
                      int n_iter, void* stream);
 
+/* ---- exact silhouette (csrc/tdr_silhouette.hip) --------------------------------------------------------------------------
+ * eval/silhouette.py:21-163 (silhouette_samples), matrix-free.  The host sorts the points by dense label id (a stable
+ * permutation `perm`, sorted -> original), so that every label is one contiguous run; `lab` (n) are the sorted ids,
+ * `starts` (L + 1) the run offsets, `w` (n, sorted order) the weights or NULL for uniform ones, `W` (L) the label weights.
+ * A scan leaves per-row partial states of n_seg column segments in `ws` (tdr_silhouette_workspace_bytes); the finish folds
+ * them in segment order and writes s (and optionally a, b) in the ORIGINAL order. */
+int64_t tdr_silhouette_workspace_bytes(int64_t n, int n_seg, int dtype_bytes);
+/* W[l] = sum of w over run l (float64 accumulation, fixed order); w == NULL: the run length */
+int tdr_silhouette_label_weights_f32(const float* w, const int64_t* starts, int64_t L, float* W, void* stream);
+int tdr_silhouette_label_weights_f64(const double* w, const int64_t* starts, int64_t L, double* W, void* stream);
+/* XT: (dp, n) row-major, the sorted points transposed and zero-padded to dp in {2, 3, 4, 8, 16} or a multiple of 16;
+ * metric 0 = euclidean, 1 = manhattan; the n columns are cut into n_seg segments of ceil(ceil(n / n_seg) / 64) * 64 columns
+ * (n_seg must be the number of such segments) */
+int tdr_silhouette_direct_f32(const float* XT, int64_t n, int dp, const int32_t* lab, const float* w, const float* W, int metric,
+                              int n_seg, void* ws, int64_t ws_bytes, void* stream);
+int tdr_silhouette_direct_f64(const double* XT, int64_t n, int dp, const int32_t* lab, const double* w, const double* W, int metric,
+                              int n_seg, void* ws, int64_t ws_bytes, void* stream);
+/* Dm: the (n, n) distance matrix in the ORIGINAL order, row stride ldd; leaves one segment */
+int tdr_silhouette_precomputed_f32(const float* Dm, int64_t ldd, int64_t n, const int64_t* perm, const int32_t* lab, const float* w,
+                                   const float* W, void* ws, int64_t ws_bytes, void* stream);
+int tdr_silhouette_precomputed_f64(const double* Dm, int64_t ldd, int64_t n, const int64_t* perm, const int32_t* lab, const double* w,
+                                   const double* W, void* ws, int64_t ws_bytes, void* stream);
+/* s = nan_to_num((b - a) / max(a, b)); a, b may be NULL */
+int tdr_silhouette_finish_f32(const void* ws, int64_t ws_bytes, int64_t n, int n_seg, const int32_t* lab, const float* w,
+                              const float* W, const int64_t* starts, const int64_t* perm, float* s, float* a, float* b, void* stream);
+int tdr_silhouette_finish_f64(const void* ws, int64_t ws_bytes, int64_t n, int n_seg, const int32_t* lab, const double* w,
+                              const double* W, const int64_t* starts, const int64_t* perm, double* s, double* a, double* b,
+                              void* stream);
+/* out[0] = mean of s in float64, fixed reduction order */
+int tdr_silhouette_mean_f32(const float* s, int64_t n, double* out, void* stream);
+int tdr_silhouette_mean_f64(const double* s, int64_t n, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
