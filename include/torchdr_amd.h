@@ -693,6 +693,26 @@ int tdr_silhouette_finish_f64(const void* ws, int64_t ws_bytes, int64_t n, int n
 int tdr_silhouette_mean_f32(const float* s, int64_t n, double* out, void* stream);
 int tdr_silhouette_mean_f64(const double* s, int64_t n, double* out, void* stream);
 
+/* ---- Lloyd k-means (csrc/tdr_kmeans.hip) ----------------------------------------------------------------------------------
+ * eval/kmeans.py (kmeans_ari).  Assignment: xp / cp are the tile images of n rows and c centres of dimension d
+ * (tdr_pack_rows_f32 for d <= 256, tdr_pack_rows_wide_f32 above); labels (n) int32 and dist (n) fp32 are the bits of
+ * tdr_knn_packed_f32 / tdr_knn_wide_f32 with k = 1, metric sqeuclidean (ties to the lower centre index); obj[0] = sum of
+ * dist in float64, fixed order (workspace: tdr_kmeans_assign_ws_bytes). */
+int64_t tdr_kmeans_assign_ws_bytes(int64_t n);
+int tdr_kmeans_assign_f32(const float* xp, int64_t n, const float* cp, int64_t c, int d, int32_t* labels, float* dist,
+                          double* obj, void* ws, int64_t ws_bytes, void* stream);
+/* Update: X (n, d) row-major, row stride ldx, labels in [0, c); 1 <= c <= n.  Writes perm (n: the rows sorted stably by
+ * label), counts (c) and the mean of every non-empty cluster into centres (c, d) (float64 sums in ascending row order,
+ * rounded once); rows of empty clusters are left as they are.  0 workspace bytes = bad arguments. */
+int64_t tdr_kmeans_update_ws_bytes(int64_t n, int64_t c, int d);
+int tdr_kmeans_update_f32(const float* X, int64_t n, int d, int64_t ldx, const int32_t* labels, int64_t c, float* centres,
+                          int32_t* counts, int32_t* perm, void* ws, int64_t ws_bytes, void* stream);
+/* faiss's empty-cluster split on (centres, counts) after an update: every empty centre ci, in ascending order, becomes a
+ * copy of the centre of cluster cj drawn with probability (size - 1) / sum(size - 1), u = splitmix64(seed ^
+ * splitmix64(iter << 32 | ci)) mod sum; even coordinates ci * (1 + 1/1024), cj * (1 - 1/1024), odd ones the other way;
+ * counts[ci] = counts[cj] / 2, counts[cj] -= counts[ci].  Nothing happens when every size is <= 1. */
+int tdr_kmeans_split_f32(float* centres, int64_t c, int d, int32_t* counts, uint64_t seed, int iter, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

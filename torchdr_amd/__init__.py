@@ -13,5 +13,5 @@ from torchdr_amd.base import DRModule  # noqa: F401,E402
 from torchdr_amd.affinity_matcher import AffinityMatcher  # noqa: F401,E402
 from torchdr_amd.neighbor_embedding.base import NeighborEmbedding, NegativeSamplingNeighborEmbedding  # noqa: F401,E402
 from torchdr_amd import eval  # noqa: F401,E402,A004
-from torchdr_amd.eval import knn_label_accuracy, neighborhood_preservation, silhouette_samples, silhouette_score  # noqa: F401,E402
+from torchdr_amd.eval import knn_label_accuracy, neighborhood_preservation, silhouette_samples, silhouette_score, kmeans_ari  # noqa: F401,E402
 from torchdr_amd.utils import binary_search, false_position  # noqa: F401,E402
